@@ -24,6 +24,8 @@ Prints ONE JSON line (rank 0).
   (five critic updates per generator update, perceptual term 0.1) — not the configuration BASELINE.json's metric is quoted on.
 * `cpu_baseline` times the CPU oracle (a port of the reference step, oracle/step.py) on the host cores: 1 warm-up + median of 3
   runs of a bounded sample.
+* `--dump-outputs DIR` writes what the LAST timed step returned (train: POH, hat_amps, target_amps, G_loss, D_loss) as DIR/<name>.npy
+  right after the timed region; inputs and weights are seeded, so two builds run with the same arguments compare output for output.
 """
 
 from __future__ import annotations
@@ -45,6 +47,7 @@ if REPO not in sys.path:
 
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X dense fp32 matrix peak (MI355X_MICROARCH.md, chip-level parameters)
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA peak (same table)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: bytes written in all
 
 
 def kernel_sources():
@@ -89,7 +92,57 @@ def parse():
                          "(n_gpus, rccl_ranks, sum of ranks) — checks the rank launch / rendezvous without running the workload (CPU test of --gpus N)")
     ap.add_argument("--mode", choices=("train", "infer"), default="train",
                     help="train: the GAN step (the benchmark metric); infer: eval-mode generator forward RGBD->POH only (informational)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most "
+                         f"{DUMP_LIMIT_BYTES >> 20} MB in all: a larger output is replaced by a fixed seeded sample of its elements); rank 0 only.  "
+                         "bench_outputs/ is the conventional, git-ignored place")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def _named_arrays(out, prefix=""):
+    """Flatten what a timed step returned (tensor / tuple / list / dict of them) into (name, tensor) pairs."""
+    if isinstance(out, torch.Tensor):
+        return [(prefix or "output", out)]
+    if isinstance(out, dict):
+        items = out.items()
+    elif isinstance(out, (tuple, list)):
+        items = ((str(i), v) for i, v in enumerate(out))
+    else:
+        return []
+    return [pair for k, v in items for pair in _named_arrays(v, f"{prefix}_{k}" if prefix else str(k))]
+
+
+def dump_outputs(out, directory, limit=DUMP_LIMIT_BYTES):
+    """Write the arrays of `out` as <directory>/<name>.npy: float64 stays float64, every other dtype becomes float32 (complex: a trailing
+    axis of 2 for the real and imaginary parts).  When the arrays exceed `limit` bytes together, each array larger than an equal share
+    of the budget is replaced by the elements at a fixed, seeded, sorted set of flat indices (the same indices on every run: two builds
+    compare element for element).  Returns {name: {"shape", "dtype", "sampled"}}: the array's own shape, and the number of elements
+    written when it was sampled (None otherwise)."""
+    import numpy as np
+
+    arrays = []
+    for name, t in _named_arrays(out):
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t.resolve_conj())
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().contiguous()
+        arrays.append((name, t.numpy()))
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for _, a in arrays)
+    share = limit // max(len(arrays), 1)
+    info = {}
+    for name, a in arrays:
+        shape, sampled = list(a.shape), None
+        if total > limit and a.nbytes > share:
+            sampled = share // a.itemsize
+            idx = np.sort(np.random.default_rng(20240611).choice(a.size, size=sampled, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        info[name] = {"shape": shape, "dtype": str(a.dtype), "sampled": sampled}
+    return info
 
 
 def kernel_source_sha16():
@@ -367,17 +420,19 @@ def main():
             sync()
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                run(rgbd)
+                last = run(rgbd)
             sync()
             dt = time.perf_counter() - t0
         if rank == 0:
+            dumped = dump_outputs({("planes" if args.planes > 0 else "POH"): last}, args.dump_outputs) if args.dump_outputs else None
             print(json.dumps({"metric": "RGBD->POH inference frames/sec (eval-mode generator forward, informational)",
                               "value": round(B * world * args.steps / dt, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
                               "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
                               "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
                               "config": {"workload": f"{args.rows}x{args.cols}x3 bs={B} generator forward (UNet + ASM back-propagation + POH encode)"
                                                      + (f" + propagation to {args.planes} planes" if args.planes > 0 else "")
-                                                     + (", hipGraph replay" if args.graph > 0 else "")}}))
+                                                     + (", hipGraph replay" if args.graph > 0 else "")},
+                              **({"dumped_outputs": dumped} if dumped is not None else {})}))
         return
 
     # LHG_MAIN_PRIORITY=high (A/B measurements): the step's main chain of kernels on a high-priority stream
@@ -390,7 +445,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        W.train_step(rgbd, tamp, tphs)
+        last = W.train_step(rgbd, tamp, tphs)
     host_enqueue = time.perf_counter() - t0  # the host's share: it has handed every launch / replay of the K steps to the stream
     sync()
     elapsed = time.perf_counter() - t0
@@ -398,6 +453,9 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = t.item()
+    # what the last timed step returned, written before any further step (graph replays overwrite their static outputs)
+    dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    del last
 
     # ---- roofline passes (every rank: the steps contain collectives).  Pass 1: the timed region's conditions.  Pass 2: second stream off.
     P = max(1, min(args.steps, args.profile_steps))
@@ -468,6 +526,8 @@ def main():
                        "grad_payload": getattr(W._sync_G, "payload", "fp32") if world > 1 else None},
             "roofline": r,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
 
     # ---- the same step with the other fp32-tensor GEMM formulations (informational; a few steps each, every rank: collectives inside)
     other, by_mode = {}, {}

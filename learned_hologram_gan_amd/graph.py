@@ -42,7 +42,7 @@ class GraphedGenerator:
 
 class GraphedTrainStep:
     """One batch of the GAN loop (watermelon._train_step: generator forward, reconstruction, `d_ratio` critic updates with the gradient
-    penalty, generator loss + backward, both Adam steps and the weight re-packs — ~900 launches on two streams) captured ONCE into a HIP
+    penalty, generator loss + backward, both Adam steps and the weight re-packs — ~900 launches) captured ONCE into a HIP
     graph and replayed with one host call per step.  ref: the per-batch body of watermelon.train, watermelon.py:207-277.
 
     What varies from step to step lives in static device buffers the captured kernels read: the batch (RGBD, target amplitude / phase),
@@ -51,6 +51,9 @@ class GraphedTrainStep:
     for the step counts this replay stands for, learning rate, gradient scale: lhg_adam_step_scaled reads them from device memory).
     The host draws / computes them exactly as the eager step does, stages them through pinned memory and copies them in front of the
     replay on the same stream.  Same kernels, same order, same bits as the eager step (tests/test_gpu_graph.py).
+
+    The capture records the weight gradients on the capture stream itself (hip_ops.single_stream): the eager step runs them on a second
+    stream, with the same kernels in the same order, so the replay gives the eager step's bits.
 
     Shapes are static: one instance per (batch, rows, cols).  Every GEMM geometry must have been autotuned before the capture (the
     warm-up steps do that).  Single process only: collectives are not captured (watermelon falls back to the eager step when the
@@ -89,7 +92,7 @@ class GraphedTrainStep:
         try:
             for (opt, _), consts in zip(opts, self._consts):
                 opt.device_consts, opt._consts_cursor = consts, 0
-            with torch.cuda.graph(self.graph):
+            with torch.cuda.graph(self.graph), hip_ops.single_stream():  # one chain of nodes: no fork to the weight-gradient stream
                 self.out = trainer._train_step(self.rgbd, self.tamp, self.tphs, self.idx, self.alphas)
         finally:
             for opt, _ in opts:

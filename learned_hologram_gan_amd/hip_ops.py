@@ -369,6 +369,26 @@ def join_side_stream(device=None) -> None:
             torch.cuda.current_stream(key).wait_stream(st)
 
 
+class single_stream:
+    """Weight and bias gradients on the caller's stream for the duration (``with single_stream(): capture``): the same kernels in the same
+    order as on the second stream, so the same bits, but no fork to another stream and no join back.  A captured train step is recorded
+    this way: its graph is one chain of nodes (a capture forked onto the side stream crashed the host runtime in hipGraphLaunch on ROCm 7.0).
+    The caller must have synchronised the side stream before entering (no weight gradient of an earlier pass may still be in flight)."""
+
+    def __enter__(self):
+        global SIDE_WGRAD
+        self.saved = SIDE_WGRAD, dict(_SIDE_STREAMS)
+        SIDE_WGRAD = False
+        _SIDE_STREAMS.clear()
+        return self
+
+    def __exit__(self, *exc):
+        global SIDE_WGRAD
+        SIDE_WGRAD = self.saved[0]
+        _SIDE_STREAMS.update(self.saved[1])
+        return False
+
+
 def _weight_grad(w, inputs, fn):
     """fn(slot) -> weight gradient from `inputs`: with ``slot`` None it returns a new tensor, otherwise it ACCUMULATES into ``slot``.
     Plain backward into a registered slot: run on the side stream, accumulate, return None (autograd's zero)."""

@@ -314,13 +314,15 @@ def test_bf16_gradient_payload_and_deferred_scale_world2():
 def test_bench_gpus_n_starts_n_ranks_by_itself():
     """`python bench.py --gpus 2` launched PLAINLY (no torchrun, WORLD_SIZE unset) must start two ranks itself — child processes, before
     anything touches a GPU — relay rank 0's line and fail loudly otherwise (it used to run one rank and report n_gpus 1).
-    --spawn-check keeps the ranks to the rendezvous + one all-reduce (gloo here: no GPU in this container)."""
+    --spawn-check keeps the ranks to the rendezvous + one all-reduce over gloo (set explicitly: on a one-GPU machine the default backend
+    would be RCCL, which needs one GPU per rank)."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["LHG_DIST_BACKEND"] = "gloo"
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--spawn-check", "1"], cwd=root, env=env,
                          capture_output=True, text=True, timeout=240)
     assert res.returncode == 0, res.stderr[-2000:]
