@@ -374,6 +374,18 @@ int lhg_bn_backward_chanmax(const float* gy, int ldgy, const float* x, int ldx, 
                             float* ggamma, float* gbeta, int accumulate, float* ws, float* gx_absmax,
                             const float* beta, float* gx_chanmax_partial, float* gres_chanmax_partial, float* gres_absmax,
                             lhg_stream_t s);
+/* Backward of an EVAL-mode BatchNorm (running statistics) z = act(scale*y + shift [+ res]), scale = gamma*invstd_running, given gz:
+ *   g = gz * act'(z) (mask from the forward OUTPUT z; act none, ReLU or LeakyReLU);  gy = scale * g;  gres = g (may be NULL: not written).
+ * There is no batch mean in the forward, so gy needs no reduction: ONE pass over the tensor.  `sums` (may be NULL): sum g over pixels
+ * (C floats), and with `y` (the pre-BN tensor; may be NULL) also sum g*xhat, xhat = (y - stats[c]) * stats[C + c] (2*C floats:
+ * sum g, then sum g*xhat) — d beta and d gamma; `stats` = running mean, running invstd (read only with y).  With `sums` the pass leaves
+ * partial rows in `ws` (>= 4096*C floats) and one reduce launch folds them in double.  gy_absmax: max-accumulates max|gy| as lhg_bn_backward's
+ * gx_absmax; gy_chanmax_partial (may be NULL; fp32 storage): per-channel partial maxima of gy (lhg_chanmax_partial_rows(pixels, C) x C
+ * floats, see lhg_channel_absmax_finish) — the scales of the preceding conv's two backward GEMMs.  gz, z, y, gy, gres: NHWC views with
+ * their own row pitch.  ref: F.batch_norm(training=False) via model.eval(), neural_network_components.py:26-32, discriminator.py:34-40. */
+int lhg_bn_eval_backward(const float* gz, int ldgz, const float* z, int ldz, const float* y, int ldy, long long pixels, int C,
+                         const float* scale, const float* stats, int act, float slope, float* gy, int ldgy, float* gres, int ldgres,
+                         float* sums, float* ws, float* gy_absmax, float* gy_chanmax_partial, lhg_stream_t s);
 /* Double backward of the gx output above (WGAN-GP, ref: watermelon.py:466-473):
  * given ggx (cotangent of gx) returns ggy (cotangent of gy), gx2 (cotangent of x) and
  * ggamma2 (cotangent of gamma).  ws: >= 5*4096*C floats. */

@@ -654,6 +654,83 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ gy, in
   }
 }
 
+// ------------------------------------------------------------------ BN backward with running statistics (eval mode)
+// z = act(scale*y + shift [+ res]) with scale / shift from the running statistics: no batch mean in the forward, so no mean-gradient
+// terms here and gy needs no reduction before it can be written — ONE pass over the tensor:
+//   g = gz * act'(z)   (mask from the forward output z);   gy = scale * g;   gres = g (may be null);
+//   NSUM partial rows [blockIdx.x][NSUM][C] in column_reduce's layout (reduced by reduce_partials<NSUM>): sum g, and with y sum g * xhat,
+//   xhat = (y - mean) * invstd (stats = running mean, running invstd);
+//   max|gy| -> gy_amax, per-channel partial maxima of gy -> cmax_partial (rows = gridDim.x, as bn_bwd_apply's).
+template <class T, int NSUM>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const T* __restrict__ gz, int ldgz, const T* __restrict__ z, int ldz,
+                                                          const T* __restrict__ y, int ldy, long long pixels, int C,
+                                                          const float* __restrict__ scale, const float* __restrict__ stats, int act, float slope,
+                                                          T* __restrict__ gy, int ldgy, T* __restrict__ gres, int ldgres, int lanes_c, int rows,
+                                                          float* __restrict__ partial, float* __restrict__ gy_amax, unsigned* __restrict__ cmax_partial) {
+  __shared__ float red[NSUM > 0 ? NSUM : 1][256 * 4];
+  __shared__ u32x4 cred[256];
+  const int tx = threadIdx.x % lanes_c, ty = threadIdx.x / lanes_c;
+  unsigned am = 0;
+  const unsigned seen = amax_peek(gy_amax);
+  for (int cb0 = blockIdx.y * lanes_c * 4; cb0 < C; cb0 += gridDim.y * lanes_c * 4) {  // uniform trip count: barriers inside
+    const int cb = cb0 + tx * 4;
+    const bool live = cb < C;
+    f32x4 cm = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[NSUM > 0 ? NSUM : 1];
+#pragma unroll
+    for (int k = 0; k < (NSUM > 0 ? NSUM : 1); ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (live) {
+      const f32x4 sc = ld4(scale + cb);
+      f32x4 mean = {0.f, 0.f, 0.f, 0.f}, inv = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (NSUM == 2) {
+        mean = ld4(stats + cb);
+        inv = ld4(stats + C + cb);
+      }
+      pixel_loop(
+          (long long)blockIdx.x * rows + ty, pixels, (long long)gridDim.x * rows,
+          [&](long long q) {
+            V3 v;
+            v.a = ld4(gz + (size_t)q * ldgz + cb);
+            if (act != LHG_ACT_NONE) v.b = ld4(z + (size_t)q * ldz + cb);
+            if constexpr (NSUM == 2) v.c = ld4(y + (size_t)q * ldy + cb);
+            return v;
+          },
+          [&](long long q, const V3& v) {
+            f32x4 g = v.a;
+            if (act != LHG_ACT_NONE) g *= act_grad4(v.b, act, slope);
+            if (gres) st4(gres + (size_t)q * ldgres + cb, g);
+            const f32x4 o = sc * g;
+            st4(gy + (size_t)q * ldgy + cb, o);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) cm[e] = fmaxf(cm[e], fabsf(o[e]));
+            if constexpr (NSUM >= 1) acc[0] += g;
+            if constexpr (NSUM == 2) acc[1] += g * ((v.c - mean) * inv);
+          });
+      am = max(am, __float_as_uint(fmaxf(fmaxf(cm[0], cm[1]), fmaxf(cm[2], cm[3]))));
+    }
+    if constexpr (NSUM > 0) {  // the workgroup's partial row, as column_reduce stores it
+#pragma unroll
+      for (int k = 0; k < NSUM; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[k][(ty * lanes_c + tx) * 4 + e] = acc[k][e];
+      __syncthreads();
+      if (ty == 0 && live) {
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k) {
+          f32x4 s = {0.f, 0.f, 0.f, 0.f};
+          for (int r = 0; r < rows; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += red[k][(r * lanes_c + tx) * 4 + e];
+          st4(partial + ((size_t)blockIdx.x * NSUM + k) * C + cb, s);
+        }
+      }
+      __syncthreads();
+    }
+    if (cmax_partial) channel_max_commit(cred, __builtin_bit_cast(u32x4, cm), tx, ty, lanes_c, rows, live, cmax_partial + (size_t)blockIdx.x * C + cb);
+  }
+  if (gy_amax) amax_commit(am, gy_amax, seen);
+}
+
 // ------------------------------------------------------------------ BN double backward (WGAN-GP)
 // Notation (xc = x - mean, r = invstd, M = pixels, g = gy * act'(y), q = ggx):
 //   ggy = act'(y) * gamma*r * (q - mean(q) - xc r^2 mean(q xc))
@@ -1093,6 +1170,36 @@ static int bn_backward_impl(const float* gy, int ldgy, const float* x, int ldx, 
 }
 
 template <class T>
+static int bn_eval_backward_impl(const float* gz, int ldgz, const float* z, int ldz, const float* y, int ldy, long long pixels, int C,
+                                 const float* scale, const float* stats, int act, float slope, float* gy, int ldgy, float* gres, int ldgres,
+                                 float* sums, float* ws, float* gy_absmax, float* gy_chanmax_partial, lhg_stream_t s) {
+  LHG_NHWC_OK(gz, C, ldgz, "bn_eval_backward(gz)");
+  LHG_NHWC_OK(gy, C, ldgy, "bn_eval_backward(gy)");
+  LHG_REQUIRE(act == LHG_ACT_NONE || act == LHG_ACT_RELU || act == LHG_ACT_LEAKY, "bn_eval_backward: activation %d (none, ReLU or LeakyReLU)", act);
+  if (act != LHG_ACT_NONE) LHG_NHWC_OK(z, C, ldz, "bn_eval_backward(z)");
+  if (gres) LHG_NHWC_OK(gres, C, ldgres, "bn_eval_backward(gres)");
+  LHG_REQUIRE(pixels > 0 && scale != nullptr, "bn_eval_backward: empty tensor or missing scale");
+  LHG_REQUIRE(sums == nullptr || ws != nullptr, "bn_eval_backward: sums need the workspace (4096*C floats)");
+  LHG_REQUIRE(y == nullptr || (sums != nullptr && stats != nullptr), "bn_eval_backward: y is read only for sum g*xhat: needs sums and stats");
+  if (y) LHG_NHWC_OK(y, C, ldy, "bn_eval_backward(y)");
+  LHG_REQUIRE(gy_chanmax_partial == nullptr || sizeof(T) == 4, "bn_eval_backward: per-channel maxima are measured of fp32 tensors only");
+  const ColMap cm = col_map(C);
+  const int nblk = apply_blocks(pixels, cm);  // <= 2048 rows: the partial sums fit 4096*C floats, the maxima lhg_chanmax_partial_rows rows
+  const int nsum = sums ? (y ? 2 : 1) : 0;
+  unsigned* cmax = reinterpret_cast<unsigned*>(gy_chanmax_partial);
+#define LHG_EVAL_BWD(NS)                                                                                                                       \
+  hipLaunchKernelGGL((bn_eval_bwd_kernel<T, NS>), dim3(nblk, cm.gy), dim3(256), 0, as_stream(s), as_act<T>(gz), ldgz, as_act<T>(z), ldz, as_act<T>(y), \
+                     ldy, pixels, C, scale, stats, act, slope, as_act<T>(gy), ldgy, as_act<T>(gres), ldgres, cm.lanes_c, cm.rows, ws, gy_absmax, cmax)
+  if (nsum == 2) LHG_EVAL_BWD(2);
+  else if (nsum == 1) LHG_EVAL_BWD(1);
+  else LHG_EVAL_BWD(0);
+#undef LHG_EVAL_BWD
+  if (nsum == 1) hipLaunchKernelGGL(reduce_partials<1>, dim3((C + RP_CH - 1) / RP_CH, 1), dim3(1024), 0, as_stream(s), ws, nblk, C, sums, 0);
+  else if (nsum == 2) hipLaunchKernelGGL(reduce_partials<2>, dim3((C + RP_CH - 1) / RP_CH, 2), dim3(1024), 0, as_stream(s), ws, nblk, C, sums, 0);
+  return check_launch("bn_eval_backward");
+}
+
+template <class T>
 static int bn_backward_backward_impl(const float* ggx, const float* gy, const float* x, const float* y, long long pixels, int C,
                                      const float* stats, const float* gamma, int act, float slope, float* ggy, float* gx2, float* ggamma2,
                                      float* ws, lhg_stream_t s, int phase = 0, float* sums_io = nullptr, float inv_count = 0.f) {
@@ -1347,6 +1454,12 @@ int lhg_bn_backward(const float* gy, int ldgy, const float* x, int ldx, const fl
                     float* ggamma, float* gbeta, int accumulate, float* ws, float* gx_absmax, const float* beta, lhg_stream_t s) {
   return LHG_ACT_CALL(bn_backward_impl, gy, ldgy, x, ldx, y, ldy, pixels, C, stats, gamma, act, slope, gx, ldgx, gres, ldgres, ggamma, gbeta,
                       accumulate, ws, gx_absmax, beta, s);
+}
+int lhg_bn_eval_backward(const float* gz, int ldgz, const float* z, int ldz, const float* y, int ldy, long long pixels, int C,
+                         const float* scale, const float* stats, int act, float slope, float* gy, int ldgy, float* gres, int ldgres,
+                         float* sums, float* ws, float* gy_absmax, float* gy_chanmax_partial, lhg_stream_t s) {
+  return LHG_ACT_CALL(bn_eval_backward_impl, gz, ldgz, z, ldz, y, ldy, pixels, C, scale, stats, act, slope, gy, ldgy, gres, ldgres, sums, ws,
+                      gy_absmax, gy_chanmax_partial, s);
 }
 int lhg_bn_backward_backward(const float* ggx, const float* gy, const float* x, const float* y, long long pixels, int C,
                              const float* stats, const float* gamma, int act, float slope, float* ggy, float* gx2, float* ggamma2,

@@ -1867,6 +1867,133 @@ def batch_norm_eval_affine(gamma, beta, running_mean, running_var):
     return scale, beta - running_mean * scale
 
 
+# --------------------------------------------------------------------------- batch norm with running statistics (eval mode), differentiable
+# model.eval() of the reference only switches BatchNorm to the running statistics; the module stays differentiable (frozen-BatchNorm
+# fine-tuning, a frozen critic as a loss, input gradients).  Two routes per layer, chosen by whether gamma / beta need a gradient:
+#   ConvBNEvalFn     gamma, beta frozen: conv + folded affine + activation in ONE GEMM epilogue, exactly the inference call (same bits);
+#   BatchNormEvalFn  gamma or beta trained: Conv2dFn writes the pre-BN y, lhg_bn_apply applies the running-statistics affine.
+# Both backwards run lhg_bn_eval_backward (one pass: g = gz act'(z), gy = scale g; the per-channel sums only when a parameter wants them).
+# Eval mode changes no BatchNorm state (no running-statistics update, no batch count).  Double backward is not implemented.
+def _no_double_backward(name):
+    if torch.is_grad_enabled():
+        raise NotImplementedError(f"{name}: double backward through an eval-mode BatchNorm (running statistics) is not implemented")
+
+
+def bn_eval_backward_raw(gz, z, y, scale, stats, act, slope, want_res, want_sums):
+    """lhg_bn_eval_backward; no autograd.  Returns (gy, gres | None, sums | None): sums = [sum g] or, with ``y`` (the pre-BN tensor),
+    [sum g, sum g*xhat] (2*C floats).  gy is the gy operand of the preceding conv's two backward GEMMs: the pass measures max|gy| and its
+    per-channel partial maxima on the way out."""
+    pg, N, H, W, Cc, ldg = nhwc(gz)
+    pz, _, _, _, _, ldz = nhwc(z)
+    py, ldy = (None, 0)
+    if y is not None:
+        py, _, _, _, _, ldy = nhwc(y)
+    pixels = N * H * W
+    gy = new_nhwc(N, H, W, Cc, gz.device)
+    gres = new_nhwc(N, H, W, Cc, gz.device) if want_res else None
+    sums = torch.empty(((2 if y is not None else 1) * Cc,), dtype=torch.float32, device=gz.device) if want_sums else None
+    ws = _bn_ws(Cc, gz.device, 4096) if want_sums else None
+    gy_amax = fused_absmax_slot(gz.device)
+    cm = chanmax_dest(Cc, pixels, gz.device)
+    if cm is not None and cm.finish:  # (LHG_CHANMAX_IN_LAUNCH: the pass leaves partial rows only; a weight gradient measures gy itself)
+        cm = None
+    call("lhg_bn_eval_backward", pg, ldg, pz, ldz, py, ldy, pixels, Cc, ptr(scale), ptr(stats), act, float(slope), ptr(gy), Cc, ptr(gres), Cc,
+         ptr(sums), ptr(ws), ptr(gy_amax), cm.ptr if cm else None, stream_ptr())
+    tag_absmax(gy, gy_amax)
+    if cm is not None:
+        cm.commit(gy)
+    return gy, gres, sums
+
+
+def _deliver_small_grad(p, g):
+    """Gradient ``g`` of a bias / BatchNorm affine parameter: added to its flat-buffer slot (None to autograd) or returned."""
+    slot = _small_grad_slot(p)
+    if slot is None:
+        return g
+    slot.add_(g)
+    note_contribution(p)
+    return None
+
+
+class ConvBNEvalFn(TrackedFunction):
+    """z = act((conv2d(x, w) + bias) * scale + shift [+ res]) with (scale, shift) of an eval-mode BatchNorm whose gamma / beta are frozen —
+    the inference call (conv2d_forward_raw with the folded affine in the epilogue), so the output has the bits of the ``no_grad`` eval
+    forward.  Backward: lhg_bn_eval_backward -> gy (and gres), then the conv's input / weight gradients; d bias = scale * sum g.
+    ref: nn.Conv2d + nn.BatchNorm2d in eval mode, neural_network_components.py:26-32, discriminator.py:34-40."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, stride, scale, shift, res, act, slope, out):
+        z = conv2d_forward_raw(x, w, bias, stride, act=act, slope=slope, scale=scale, shift=shift, res=res, out=out, measure_out=True)
+        ctx.save_for_backward(x, w, z, scale)
+        ctx.stride, ctx.act, ctx.slope, ctx.has_bias, ctx.has_res = stride, act, slope, bias is not None, res is not None
+        note_use(w, ctx.needs_input_grad[1])
+        ctx.bias = bias if (bias is not None and ctx.needs_input_grad[2]) else None
+        note_use(ctx.bias)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        _no_double_backward("ConvBNEvalFn")
+        x, w, z, scale = ctx.saved_tensors
+        want_bias = ctx.bias is not None and param_grads_wanted()
+        gy, gres, sums = bn_eval_backward_raw(_as_nhwc_view(gz), z, None, scale, None, ctx.act, ctx.slope, ctx.has_res and ctx.needs_input_grad[6],
+                                              want_bias)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gemm = not (w.shape[2] == w.shape[3] and thin_mode(w.shape[1], w.shape[0], w.shape[2], ctx.stride))
+            gy_amax = operand_absmax(gy) if gemm else None
+            gx = Conv2dInputGradFn.apply(gy, w, ctx.stride, x.shape[1], x.shape[2], x.shape[3], gy_amax, None, _feeds_gemm(x))
+        if param_grads_wanted():
+            if ctx.needs_input_grad[1]:
+                gw = _weight_grad(w, (x, gy), lambda slot: conv2d_weight_grad(x, gy, w.shape, ctx.stride, slot))
+            if want_bias:
+                gb = _deliver_small_grad(ctx.bias, scale * sums)
+        return gx, gw, gb, None, None, None, gres, None, None, None
+
+
+class BatchNormEvalFn(TrackedFunction):
+    """z = act((y - running_mean) * invstd_running * gamma + beta [+ res]) for a BatchNorm in eval mode whose gamma or beta is trained
+    (lhg_bn_apply with the running statistics as ``stats``).  Backward: lhg_bn_eval_backward with y -> gy, gres, d beta = sum g,
+    d gamma = sum g * xhat.  The running statistics are read, never written."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, running_mean, running_var, res, act, slope, out):
+        py, N, H, W, Cc, ldy = nhwc(y)
+        stats = torch.cat((running_mean, torch.rsqrt(running_var + BN_EPS))).float().contiguous()
+        z = _resolve_out(out, (N, H, W, Cc), y.device)
+        pz, _, _, _, _, ldz = nhwc(z)
+        pres, ldres = (None, 0)
+        if res is not None:
+            pres, _, _, _, _, ldres = nhwc(res)
+        z_amax = _out_amax(out, y.device)  # z is the next conv's operand
+        call("lhg_bn_apply", py, ldy, N * H * W, Cc, ptr(stats), ptr(gamma), ptr(beta), pres, ldres, act, float(slope), pz, ldz, ptr(z_amax), stream_ptr())
+        tag_absmax(z, z_amax)
+        ctx.save_for_backward(y, z, gamma, stats)
+        ctx.act, ctx.slope, ctx.has_res = act, slope, res is not None
+        ctx.gamma = gamma if ctx.needs_input_grad[1] else None
+        ctx.beta = beta if ctx.needs_input_grad[2] else None
+        note_use(ctx.gamma)
+        note_use(ctx.beta)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        _no_double_backward("BatchNormEvalFn")
+        y, z, gamma, stats = ctx.saved_tensors
+        Cc = y.shape[-1]
+        scale = gamma * stats[Cc:]
+        want_sums = (ctx.gamma is not None or ctx.beta is not None) and param_grads_wanted()
+        gy, gres, sums = bn_eval_backward_raw(_as_nhwc_view(gz), z, y if want_sums else None, scale, stats, ctx.act, ctx.slope,
+                                              ctx.has_res and ctx.needs_input_grad[5], want_sums)
+        ggamma = gbeta = None
+        if want_sums:
+            if ctx.gamma is not None:
+                ggamma = _deliver_small_grad(ctx.gamma, sums[Cc:])
+            if ctx.beta is not None:
+                gbeta = _deliver_small_grad(ctx.beta, sums[:Cc])
+        return (gy if ctx.needs_input_grad[0] else None), ggamma, gbeta, None, None, gres, None, None, None
+
+
 # --------------------------------------------------------------------------- pooling
 class MaxPool2x2Fn(Function):
     @staticmethod

@@ -90,6 +90,7 @@ _SIGNATURES = {
     "lhg_bn_stats": [_p, _ll, _i, _i, _p, _p, _p, _f, _f, _p, _p],
     "lhg_bn_apply": [_p, _i, _ll, _i, _p, _p, _p, _p, _i, _i, _f, _p, _i, _p, _p],
     "lhg_bn_backward": [_p, _i, _p, _i, _p, _i, _ll, _i, _p, _p, _i, _f, _p, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p],
+    "lhg_bn_eval_backward": [_p, _i, _p, _i, _p, _i, _ll, _i, _p, _p, _i, _f, _p, _i, _p, _i, _p, _p, _p, _p, _p],
     "lhg_bn_backward_backward": [_p, _p, _p, _p, _ll, _i, _p, _p, _i, _f, _p, _p, _p, _p, _p],
     "lhg_bn_backward_sums": [_p, _i, _p, _i, _p, _i, _ll, _i, _p, _p, _i, _f, _p, _p, _p, _p],
     "lhg_bn_backward_apply": [_p, _i, _p, _i, _p, _i, _ll, _i, _p, _p, _p, _f, _i, _f, _p, _i, _p, _i, _p, _p, _p],

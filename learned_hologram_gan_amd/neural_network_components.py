@@ -12,7 +12,6 @@ constructor argument with the value the hot path uses.
 from __future__ import annotations
 
 import os
-import warnings
 
 import torch
 from torch import nn
@@ -39,9 +38,27 @@ def _bn_eval_affine(bn: nn.BatchNorm2d):
     return affine
 
 
-def _warn_eval_grad(name):
-    warnings.warn(f"{name}: eval-mode forward runs the fused inference kernels and is not differentiable "
-                  "(the reference only evaluates under torch.no_grad())", stacklevel=3)
+def eval_grad_wanted(module: nn.Module, *inputs) -> bool:
+    """Eval-mode forward that autograd records: grad mode on and an input or a parameter of ``module`` requires grad.  Otherwise eval mode
+    runs the inference kernels under no_grad (the same kernels and bits as ``with torch.no_grad()``)."""
+    if module.training or not torch.is_grad_enabled():
+        return False
+    return any(t is not None and t.requires_grad for t in inputs) or any(p.requires_grad for p in module.parameters())
+
+
+def _conv_bn_eval(conv: nn.Conv2d, bn: nn.BatchNorm2d, x, stride, res, out, act=ACT_RELU, slope=0.0, cached=True):
+    """act(BN_running(conv(x)) [+ res]), differentiable.  Frozen gamma / beta: the conv with the folded affine in its epilogue (the
+    inference call, same bits; ``cached``: the affine from _bn_eval_affine, as the caller's inference path takes it); a trained gamma or
+    beta needs the pre-BN conv output for d gamma: the conv, then the BatchNorm op (nothing cached)."""
+    if not (bn.weight.requires_grad or bn.bias.requires_grad):
+        if cached:
+            scale, shift = _bn_eval_affine(bn)
+        else:
+            with torch.no_grad():
+                scale, shift = ops.batch_norm_eval_affine(bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        return ops.ConvBNEvalFn.apply(x, conv.weight, conv.bias, stride, scale, shift, res, act, slope, out)
+    y = ops.Conv2dFn.apply(x, conv.weight, conv.bias, stride, None)  # (no "feeds_bn": the bias gradient is scale * sum g here, not zero)
+    return ops.BatchNormEvalFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, res, act, slope, out)
 
 
 _PENDING_COUNTERS: list = []
@@ -99,8 +116,11 @@ class ResidualBlock(nn.Module):
             skip = ops.Conv2dFn.apply(xs, c3.weight, c3.bias, self.strides, None) if c3 is not None else xs
             _count_batch(b1, b2)
             return ops.BatchNormTrainFn.apply(y, b2.weight, b2.bias, b2.running_mean, b2.running_var, skip, ACT_RELU, 0.0, out)
-        if torch.is_grad_enabled() and (x.requires_grad or c1.weight.requires_grad):
-            _warn_eval_grad("ResidualBlock")
+        if eval_grad_wanted(self, x):
+            # eval mode under autograd: the running-statistics BatchNorms as differentiable ops (hip_ops.ConvBNEvalFn / BatchNormEvalFn)
+            y = _conv_bn_eval(c1, b1, x, self.strides, None, None)
+            skip = ops.Conv2dFn.apply(x, c3.weight, c3.bias, self.strides, None) if c3 is not None else x
+            return _conv_bn_eval(c2, b2, y, 1, skip, out)
         with torch.no_grad():
             s1, t1 = _bn_eval_affine(b1)
             s2, t2 = _bn_eval_affine(b2)
@@ -200,14 +220,14 @@ class UNet(nn.Module):
     def _block(seq_entry):
         return seq_entry[0] if isinstance(seq_entry, nn.Sequential) else seq_entry
 
-    def _up(self, convt: nn.ConvTranspose2d, x, out: OutSlot):
-        if self.training:
+    def _up(self, convt: nn.ConvTranspose2d, x, out: OutSlot, record: bool):
+        if record:
             return ops.ConvTranspose2x2Fn.apply(x, convt.weight, convt.bias, out)
         with torch.no_grad():
             return ops.ConvTranspose2x2Fn.apply(x, convt.weight, convt.bias, out)
 
-    def _cat(self, skip, up, buf, share):
-        if self.training:
+    def _cat(self, skip, up, buf, share, record: bool):
+        if record:
             return ops.CatViewsFn.apply(skip, up, OutSlot(buf, share))
         return share.tag(buf)
 
@@ -221,6 +241,8 @@ class UNet(nn.Module):
         direct = (_THIN_NCHW and not self.training and not torch.is_grad_enabled() and X.is_cuda and X.dtype == torch.float32 and blk1.strides == 1
                   and blk1.convolution_layer_3 is not None and ops.activation_storage() == "fp32"
                   and ops.thin_mode(self.in_channels, 64, 3, 1) == 1 and ops.thin_mode(self.in_channels, 64, 1, 1) == 1)
+        # train mode, or an eval-mode forward that autograd records: the transposed convs, concatenations and the head as autograd ops
+        record = self.training or eval_grad_wanted(self, X)
         x = None if direct else ops.ToNHWC.apply(X, 32)
         new = lambda h, w, c: ops.new_nhwc(N, h, w, c, dev)  # noqa: E731  (fp32, or bf16 in the bf16 storage mode)
         buf4, buf3, buf2, buf1 = new(H, W, 128), new(H // 2, W // 2, 256), new(H // 4, W // 4, 512), new(H // 8, W // 8, 1024)
@@ -239,17 +261,17 @@ class UNet(nn.Module):
         e4 = self._block(self.encoder4[1]).forward_nhwc(p3, OutSlot(buf1[..., :512], sh1))
         p4, e4 = pool_skip(e4)
         b = self._block(self.bottleneck[1]).forward_nhwc(p4)
-        u = self._up(self.bottleneck[2], b, OutSlot(buf1[..., 512:], sh1))
-        d = self._block(self.decoder1[0]).forward_nhwc(self._cat(e4, u, buf1, sh1))
-        u = self._up(self.decoder1[1], d, OutSlot(buf2[..., 256:], sh2))
-        d = self._block(self.decoder2[0]).forward_nhwc(self._cat(e3, u, buf2, sh2))
-        u = self._up(self.decoder2[1], d, OutSlot(buf3[..., 128:], sh3))
-        d = self._block(self.decoder3[0]).forward_nhwc(self._cat(e2, u, buf3, sh3))
-        u = self._up(self.decoder3[1], d, OutSlot(buf4[..., 64:], sh4))
-        d = self._block(self.decoder4).forward_nhwc(self._cat(e1, u, buf4, sh4))
+        u = self._up(self.bottleneck[2], b, OutSlot(buf1[..., 512:], sh1), record)
+        d = self._block(self.decoder1[0]).forward_nhwc(self._cat(e4, u, buf1, sh1, record))
+        u = self._up(self.decoder1[1], d, OutSlot(buf2[..., 256:], sh2), record)
+        d = self._block(self.decoder2[0]).forward_nhwc(self._cat(e3, u, buf2, sh2, record))
+        u = self._up(self.decoder2[1], d, OutSlot(buf3[..., 128:], sh3), record)
+        d = self._block(self.decoder3[0]).forward_nhwc(self._cat(e2, u, buf3, sh3, record))
+        u = self._up(self.decoder3[1], d, OutSlot(buf4[..., 64:], sh4), record)
+        d = self._block(self.decoder4).forward_nhwc(self._cat(e1, u, buf4, sh4, record))
         head = self.final_layer[0]
         flush_batch_counters()
-        if self.training:
+        if record:
             return ops.SigmoidHeadFn.apply(d, head.weight, head.bias)
         with torch.no_grad():
             return ops.conv2d_forward_raw(d, head.weight, head.bias, 1, act=ops.ACT_SIGMOID, planar=True)

@@ -7,7 +7,7 @@ from torch import nn
 
 from .. import hip_ops as ops
 from ..hip_ops import ACT_LEAKY
-from ..neural_network_components import _count_batch, flush_batch_counters
+from ..neural_network_components import _conv_bn_eval, _count_batch, eval_grad_wanted, flush_batch_counters
 
 
 class WGANGPDiscriminator192(nn.Module):
@@ -46,6 +46,12 @@ class WGANGPDiscriminator192(nn.Module):
                 h = ops.BatchNormTrainFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, None, ACT_LEAKY, 0.2, None)
                 _count_batch(bn)
             flush_batch_counters()
+            s = ops.Conv2dFn.apply(h, self.conv.weight, self.conv.bias, 1, None)
+        elif eval_grad_wanted(self, x):
+            # eval mode under autograd (a frozen critic as a loss, input gradients): the running-statistics BatchNorms as differentiable ops
+            h = ops.ConvBiasActFn.apply(h, c1.weight, c1.bias, 1, ACT_LEAKY, 0.2)
+            for blk in (self.block2, self.block3, self.block4, self.block5, self.block6):
+                h = _conv_bn_eval(blk[0], blk[1], h, blk[0].stride[0], None, None, ACT_LEAKY, 0.2, cached=False)  # (as the inference path: no cache)
             s = ops.Conv2dFn.apply(h, self.conv.weight, self.conv.bias, 1, None)
         else:
             with torch.no_grad():
